@@ -11,6 +11,7 @@ drop-in Python API (skyeye.core.models / skyeye.utils.metrics), i.e. through the
     python bench.py --model skyeye_s_ha              # config 3 (attention heads on)
     python bench.py --model skyeye_l                 # config 4, one GPU's shard
     python bench.py --model skyeye_l --precision fp8 --size 1536   # config 5, one GPU's shard
+    python bench.py --dump-outputs DIR               # also DIR/rows.npy, DIR/counts.npy: the last timed step's boxes (seeded frames)
 
 N > 1: one process per GPU, every rank runs the same per-GPU batch (weak scaling, images are independent units),
 then an RCCL all-gather of the fixed-capacity box buffers so every rank holds all results (BASELINE north_star).
@@ -62,7 +63,12 @@ def parse():
     ap.add_argument("--no-pipeline", action="store_true", help="NMS of a batch strictly behind its own forward pass (default: the NMS of batch k runs beside the "
                     "forward pass of batch k + 1, SkyEyeDetector.detect_nms_pipelined; every batch's NMS is inside the timed region)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short legs of configs 3, 4 (shard), 5 (shard) behind the headline measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline leg's last timed step returned (NMS rows and counts "
+                    "of every image) as DIR/<name>.npy, float32 / float64, so that two builds can be compared output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def spawn_workers(a):
@@ -167,6 +173,25 @@ def plan_gflop_per_frame(model, x):
     return model._engine([xi]).stats()["flops"] / xi.shape[0] / 1e9
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: rows [images, max_det, 7] as float32 (rows past an image's count are zero, k_nms.hip) and counts [images] as float64.
+    Past DUMP_LIMIT_BYTES a fixed, seeded sample of images is written, with their indices in image_index.npy."""
+    import numpy as np
+    arrays = {"rows": outputs["rows"].float().cpu().numpy(), "counts": outputs["counts"].cpu().numpy().astype(np.float64)}
+    n = arrays["counts"].shape[0]
+    per_image = sum(v.nbytes for v in arrays.values()) / n
+    if per_image * n > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, int((DUMP_LIMIT_BYTES - 8 * n) // per_image), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["image_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -217,7 +242,7 @@ def main():
     from skyeye.utils.torch_utils import capture_graph
     from skyeye.distributed import BoxExchange
 
-    def timed_leg(model_name, precision, size, steps, warmup):
+    def timed_leg(model_name, precision, size, steps, warmup, keep_outputs=False):
         """Build + calibrate a detector, capture forward + NMS (+ the RCCL all-gather when world > 1) and time `steps` steps between
         barriers; returns everything the report needs."""
         model, P = build_model(model_name, precision, dev)
@@ -392,6 +417,8 @@ def main():
         fence()
         dt = time.perf_counter() - t0
         dt_rank = dt
+        # the last step's result, copied before the strict-order and latency steps below write the same buffers again
+        outputs = {"rows": rows.clone(), "counts": counts.clone()} if keep_outputs else None
         ag_ms = sum(e0.elapsed_time(e1) for e0, e1 in ag["ev"]) / max(len(ag["ev"]), 1) if ag["ev"] else None
         ag["ev"].clear()
         rank_fps = None
@@ -423,14 +450,17 @@ def main():
                       "what": "forward then its own NMS" + (" then the all-gather" if world > 1 else "") + ", one graph replay per batch (--no-pipeline)"}
             ag["ev"].clear()
         return dict(model=model, P=P, x=x, frames_np=frames_np, step=sync_step, graph=graph, dt=dt, counts=counts, pipelined=pipelined,
-                    steps_per_replay=2 * npair if (pipelined and (pair is not None or mpairs is not None)) else 1, strict=strict, allgather_ms=ag_ms, rank_fps=rank_fps)
+                    steps_per_replay=2 * npair if (pipelined and (pair is not None or mpairs is not None)) else 1, strict=strict, allgather_ms=ag_ms,
+                    rank_fps=rank_fps, outputs=outputs)
 
     def fence():
         if multi:
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    leg = timed_leg(a.model, a.precision, a.size, a.steps, a.warmup)
+    leg = timed_leg(a.model, a.precision, a.size, a.steps, a.warmup, keep_outputs=bool(a.dump_outputs))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, leg.pop("outputs"))
     model, P, x, frames_np, step, graph, dt, counts = (leg[k] for k in ("model", "P", "x", "frames_np", "step", "graph", "dt", "counts"))
     B, S = a.batch, a.size
     kept_mean = float(counts.float().mean().item())

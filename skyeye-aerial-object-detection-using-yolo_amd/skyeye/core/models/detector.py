@@ -216,7 +216,8 @@ class SkyEyeDetector(NativeModule):
         """A two-deep software pipeline over a stream of batches (an extension; validate.py:245-255 / detect.py:140-145 run the pair
         strictly one after the other): the forward pass of THIS batch is enqueued beside the non_max_suppression of the PREVIOUS one,
         which otherwise runs alone behind the join -- a chain of seven small kernels on a few CUs, 0.145 of 4.35 ms on the benchmark
-        batch.  Returns (rows [B, max_det, 7], counts [B]) of the previous batch, or None for the first call; ``detect_nms_flush()``
+        batch.  With ``parallel_slices`` that NMS runs on the last slice's stream behind the slice's forward pass, beside the other
+        slices.  Returns (rows [B, max_det, 7], counts [B]) of the previous batch, or None for the first call; ``detect_nms_flush()``
         returns the last batch's.  Two sets of detection / NMS buffers alternate (``parity`` 0 / 1; given explicitly when the two
         forms are captured as two hipGraphs, else it toggles per call).  Needs ``reuse_output_buffers(True)``.  Same results as
         ``detect_nms`` on every batch (tests/test_gpu_slices.py).  ``out``: (rows, counts) for the PREVIOUS batch's boxes (the views of
@@ -245,7 +246,9 @@ class SkyEyeDetector(NativeModule):
             finally:
                 self.__dict__["_out_slot"] = 0
         prev = st["pending"] if parity is None else st.get(("det", 1 - p))
-        result = None
+        nsl = self.__dict__.get("_slices", 1)
+        sliced = nsl > 1 and self._sliceable([xi], nsl)
+        result, post, joined = None, None, False
         if prev is not None and prev.shape[0] != B:                            # batch size changed: the previous batch's NMS into fresh tensors
             result = nms_raw(prev, conf_threshold, iou_threshold, max_detections=max_detections, **nms_kw)
         elif prev is not None:
@@ -254,16 +257,28 @@ class SkyEyeDetector(NativeModule):
             if bufs is None:
                 bufs = self._out_cache[ck] = (torch.empty((B, int(max_detections), 7), dtype=torch.float32, device=dev),
                                               torch.empty((B,), dtype=torch.int32, device=dev))
-            side.wait_stream(cur)                                              # fork: the previous batch's detections are complete on `cur`
-            with torch.cuda.stream(side):
-                nms_raw(prev, conf_threshold, iou_threshold, max_detections=max_detections, out=bufs[0], counts=bufs[1], **nms_kw)
+            if sliced:
+                # on the last slice's stream behind that slice's forward pass, not on a stream of its own: captured, a third independent
+                # chain beside the two slice chains gives a hipGraph whose replay segfaults in this runtime's hipGraphLaunch (graphs of two
+                # independent chains, as detect_nms makes, replay)
+                def post(i, lo, hi, views):
+                    if i == nsl - 1:
+                        nms_raw(prev, conf_threshold, iou_threshold, max_detections=max_detections, out=bufs[0], counts=bufs[1], **nms_kw)
+            else:
+                side.wait_stream(cur)                                          # fork: the previous batch's detections are complete on `cur`
+                with torch.cuda.stream(side):
+                    nms_raw(prev, conf_threshold, iou_threshold, max_detections=max_detections, out=bufs[0], counts=bufs[1], **nms_kw)
+                joined = True
             result = bufs
         self.__dict__["_out_slot"] = 1 + p
         try:
-            det = self._run([xi], skip=(1, 2, 3))[0]
+            if sliced:
+                det = self._run_sliced([xi], None, (1, 2, 3), nsl, post=post)[0]   # (the slice streams are joined into `cur` there)
+            else:
+                det = self._run([xi], skip=(1, 2, 3))[0]
         finally:
             self.__dict__["_out_slot"] = 0
-        if result is not None and prev.shape[0] == B:
+        if joined:
             cur.wait_stream(side)                                              # join
         st[("det", p)] = det
         st["pending"] = det
